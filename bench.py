@@ -2,6 +2,7 @@
 """bench.py -- landmark-hash extraction throughput on MI355X (the BASELINE.json metric).
 
     python bench.py --gpus 1 --steps K --warmup W            (single GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full     (everything the line carries: see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,6 +22,12 @@ used only for the barrier, the max-over-ranks of the elapsed time and the AND of
 Batches are kept in flight the way a bulk ingest would: a few contexts share a spectral-stage stream and a
 scan-stage stream (afp_set_stage_streams), so batch i+1's STFT runs beside batch i's scan; every step is
 still a complete pass and `ms_per_step_one_context` is the same K steps strictly back to back.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the rows of the last timed step
+written out when `--dump-outputs DIR` asks for them, and the line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`
+and `ms_per_step` (plus the workload's configuration).  Everything below -- the one-context rerun, clock / power sensors,
+per-kernel timings and roofline, parity against the CPU oracle, the CPU baselines, ranks_seen and every extra workload --
+runs only with `--full`.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the longest of k_stft / k_scan),
 measured with HIP events on the launch stream inside this script; `cpu_baseline` times the numpy oracle
@@ -349,9 +356,10 @@ class Runner(object):
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, wl, d_pcm, offsets, steps, warmup, overlap=True, staged=-1, inflight=0, keep_result=True):
+    def measure(self, wl, d_pcm, offsets, steps, warmup, overlap=True, staged=-1, inflight=0, keep_result=True, full=True):
         """W untimed warmup steps, then exactly K timed steps bracketed by barrier + synchronize; returns a dict.
-        `timed_res` = the BatchResult of the last timed step (fetched right after the timed region, outside it)."""
+        `timed_res` = the BatchResult of the last timed step (fetched right after the timed region, outside it).
+        full=False stops there: no one-context rerun, clock probe, power sampling or per-kernel timing."""
         args = self.args
         if staged < 0:
             staged = 1          # (r02: since k_stft needs 25 KB of LDS the staged arrangement also wins on the multi-shift C5)
@@ -399,6 +407,9 @@ class Runner(object):
             last = exs[(steps - 1) % len(exs)]
             timed_res = last.fetch(len(offsets) - 1, True, False)
             timed_res.path = last.path_stats()
+        staged_n = len(self.stage_sets[0]) if (staged and len(exs) > 1) else 0
+        if not full:
+            return dict(elapsed=elapsed, nh=nh, nctx=len(exs), staged=staged_n, timed_res=timed_res)
         # the same K steps strictly back to back on one context (no overlap between batches)
         self.barrier()
         ts0 = time.perf_counter()
@@ -436,8 +447,7 @@ class Runner(object):
         ex.set_timing(False)
         kern_ms = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in tm.items()}
         return dict(elapsed=elapsed, nh=nh, serial_ms=serial_ms, kern_ms=kern_ms, nctx=len(exs),
-                    staged=(len(self.stage_sets[0]) if (staged and len(exs) > 1) else 0), mhz=mhz, power=power,
-                    timed_res=timed_res)
+                    staged=staged_n, mhz=mhz, power=power, timed_res=timed_res)
 
 
 def numa_of_gpu(torch, dev):
@@ -937,6 +947,11 @@ def parse_args():
     ap.add_argument('--stages', type=int, default=3, help='2: spectral | scan+pair;  3: spectral | scan | pair')
     ap.add_argument('--scan-streams', type=int, default=1, help='independent scan-stage streams (contexts alternate)')
     ap.add_argument('--scan-prio', type=int, default=-1, help='torch stream priority of the scan-stage stream (-1 = high)')
+    ap.add_argument('--full', action='store_true', help='everything besides the headline: one-context rerun, sensors, per-kernel '
+                    'timings and roofline, parity against the CPU oracle, CPU baselines, ranks_seen and the extra workloads '
+                    '(the --no-* switches above narrow what --full runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write the rows of the last timed '
+                    'step (rank 0) as DIR/*.npy in float64, at most 64 MB (a fixed seeded sample of whole clips beyond that)')
     ap.add_argument('--cu-split', type=int, default=-1, help='staged mode: compute units given to the scan / pairing stages (the '
                     'spectral stage gets the rest): the stages of consecutive batches run on DISJOINT CUs instead of time-sharing '
                     'all of them; 0 = no partition; -1 = default')
@@ -1027,7 +1042,7 @@ def open_bench(args):
     # synthetic input: c3 / c5 / c4_slice share the pool -- clip i of a workload with shorter clips is the first samples of pool clip i
     B.npool = min(args.pool, max(B.nclips, 1))
     B.pool = synth_pool(B.npool, B.nsamp, seed0=1000003 * B.rank)
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import afp_oracle as O          # the checker (and the CPU baseline when no reference tree is given)
         B.O = O
     return B
@@ -1074,7 +1089,7 @@ def headline(B):
     B.d_pcm, B.offsets = B.resident(B.nclips, B.nsamp)
     B.torch.cuda.synchronize()
     m = B.m = B.R.measure(wl, B.d_pcm, B.offsets, args.steps, args.warmup, overlap=not args.no_overlap, staged=args.staged,
-                          inflight=args.inflight)
+                          inflight=args.inflight, keep_result=bool(args.full or args.dump_outputs), full=args.full)
     elapsed, tot_hashes, audio_s_per_step = reduce_job_stats(m['elapsed'], float(m['nh']), B.nclips * wl['secs'], B.dist, B.rdev)
     ms_per_step = elapsed / args.steps * 1e3
     xrt = audio_s_per_step * args.steps / elapsed
@@ -1086,12 +1101,45 @@ def headline(B):
                            sharding='clips/rank, no collective'),
                audio_sec_per_sec=round(xrt, 1), audio_sec_per_sec_per_gpu=round(xrt / B.world, 1),
                hashes_per_step=tot_hashes, batches_in_flight=m['nctx'], staged=m['staged'],
-               cu_split=(B.R.cu_split() if m['staged'] else 0),
-               ms_per_step_one_context=round(m['serial_ms'], 4), shader_mhz_under_load=m['mhz'],
-               power_under_load=m['power'], build_id=B.BID,
-               roofline=roofline_obj(args.workload, wl, B.nclips, B.nsamp, m['nh'], ms_per_step, m['kern_ms'], m['mhz'], B.BID),
+               cu_split=(B.R.cu_split() if m['staged'] else 0), build_id=B.BID,
                runtime=dict(audfprint_amd.runtime_info(), host_threads=int(B.lib.load().afp_host_threads())))
+    if args.full:
+        out.update(ms_per_step_one_context=round(m['serial_ms'], 4), shader_mhz_under_load=m['mhz'], power_under_load=m['power'],
+                   roofline=roofline_obj(args.workload, wl, B.nclips, B.nsamp, m['nh'], ms_per_step, m['kern_ms'], m['mhz'], B.BID))
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, d, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the (time, hash) rows of every clip
+    (BatchResult.hashes, sorted unique per clip) and the per-clip row offsets -- as float64 .npy files (exact for int32).
+    If all clips do not fit in `max_bytes`, a fixed seeded sample of whole clips is written: its size is a power of two
+    chosen with a 2x margin over the mean row count, so two builds that agree pick the same clips."""
+    n = int(res.nclips)
+    counts = np.diff(res.hash_offsets)
+    row_bytes = 2 * 8
+    if (int(res.hash_offsets[-1]) * row_bytes + 3 * 8 * (n + 1)) <= max_bytes:
+        clips = np.arange(n)
+    else:
+        per_clip = 2.0 * max(1.0, float(counts.mean())) * row_bytes + 3 * 8
+        k = 1
+        while 2 * k <= n and 2 * k * per_clip <= max_bytes:
+            k *= 2
+        order = np.random.RandomState(0).permutation(n)
+        while True:
+            clips = np.sort(order[:k])
+            if int(counts[clips].sum()) * row_bytes + 3 * 8 * (k + 1) <= max_bytes or k == 1:
+                break
+            k //= 2
+    offs = np.zeros(len(clips) + 1, np.int64)
+    np.cumsum(counts[clips], out=offs[1:])
+    rows = res.hashes if len(clips) == n else np.concatenate([res.clip_hashes(i) for i in clips]).reshape(-1, 2)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'hashes.npy'), np.asarray(rows, np.float64).reshape(-1, 2))
+    np.save(os.path.join(d, 'hash_offsets.npy'), offs.astype(np.float64))
+    np.save(os.path.join(d, 'clips.npy'), clips.astype(np.float64))
 
 
 def ranks_seen(B, out):
@@ -1801,6 +1849,21 @@ def main():
     start_ranks_ourselves(args)
     B = open_bench(args)
     out = headline(B)                       # W warm-up + K timed steps of the hot path; the contract fields of the line
+    if args.dump_outputs and B.rank == 0:
+        dump_outputs(B.m['timed_res'], args.dump_outputs)
+    if args.full:
+        full_extras(B, out)
+    if B.rank == 0:
+        B.emit(out)
+    os.close(B.json_fd)
+    if B.dist is not None:
+        B.dist.barrier()
+        B.dist.destroy_process_group()
+
+
+def full_extras(B, out):
+    """--full: everything the line carries besides the headline (every rank takes part in the same collectives)."""
+    args = B.args
     ranks_seen(B, out)
     guard = None
     if B.O is not None:
@@ -1823,12 +1886,6 @@ def main():
             B.line_guard.disarm()
     elif B.rank == 0:
         single_gpu_extras(B, out, guard)
-    if B.rank == 0:
-        B.emit(out)
-    os.close(B.json_fd)
-    if B.dist is not None:
-        B.dist.barrier()
-        B.dist.destroy_process_group()
 
 
 if __name__ == '__main__':

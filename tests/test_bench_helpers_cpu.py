@@ -97,3 +97,33 @@ def test_cgroup_limit_is_a_number_or_none(bench, monkeypatch):
     assert 1 <= n <= (os.cpu_count() or 1)
     monkeypatch.setattr(bench, 'cgroup_cpu_limit', lambda: 2.5)
     assert bench.effective_cpus() == min(3, os.cpu_count() or 1, len(os.sched_getaffinity(0)))
+
+
+def test_plain_and_full_switches(bench, monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == 'out'
+
+
+def test_dump_outputs_writes_the_rows_as_float64_within_the_budget(bench, tmp_path):
+    rng = np.random.RandomState(5)
+    rows = [rng.randint(0, 1 << 20, size=(int(n), 2)) for n in rng.randint(0, 300, size=64)]
+    res = _result(rows)
+    bench.dump_outputs(res, str(tmp_path / 'all'))
+    h, off, cl = (np.load(str(tmp_path / 'all' / f)) for f in ('hashes.npy', 'hash_offsets.npy', 'clips.npy'))
+    assert h.dtype == off.dtype == cl.dtype == np.float64
+    assert np.array_equal(h, res.hashes) and np.array_equal(off, res.hash_offsets) and np.array_equal(cl, np.arange(64))
+    # over the budget: a fixed sample of whole clips, the same one from run to run
+    budget = 16 * int(res.hash_offsets[-1]) // 5
+    for sub in ('s1', 's2'):
+        bench.dump_outputs(res, str(tmp_path / sub), max_bytes=budget)
+    h, off, cl = (np.load(str(tmp_path / 's1' / f)) for f in ('hashes.npy', 'hash_offsets.npy', 'clips.npy'))
+    assert sum(os.path.getsize(str(tmp_path / 's1' / f)) - 128 for f in os.listdir(str(tmp_path / 's1'))) <= budget
+    assert 1 <= len(cl) < 64 and np.all(np.diff(cl) > 0)
+    for k, c in enumerate(cl.astype(int)):
+        assert np.array_equal(h[int(off[k]):int(off[k + 1])], res.clip_hashes(c))
+    for f in ('hashes.npy', 'hash_offsets.npy', 'clips.npy'):
+        assert np.array_equal(np.load(str(tmp_path / 's1' / f)), np.load(str(tmp_path / 's2' / f)))

@@ -1,14 +1,12 @@
 """CPU: the drop-in module's surface, file formats and pickling (no GPU compute)."""
 import os
 import pickle
-import sys
 
 import numpy as np
 import pytest
 
 import audfprint_amd.audfprint_analyze as M
 
-REF = '/root/reference'
 
 REF_NAMES = ['PRECOMPEXT', 'PRECOMPPKEXT', 'locmax', 'DENSITY', 'OVERSAMP', 'N_FFT', 'N_HOP', 'HPF_POLE',
              'F1_BITS', 'DF_BITS', 'DT_BITS', 'B1_MASK', 'B1_SHIFT', 'DF_MASK', 'DF_SHIFT', 'DT_MASK',
@@ -33,35 +31,49 @@ def test_module_surface():
     assert M.Analyzer(70.0).density == 70.0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not mounted')
+def _ref():
+    """what the reference module answered (tests/golden/make_golden_refcases.py -> tests/golden/reference_dropin.npz)"""
+    import json
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_dropin.npz'))
+    return z, json.loads(str(z['meta']))
+
+
+def _scalar(v):
+    return v['bytes'].encode('latin-1') if isinstance(v, dict) else v
+
+
+def dropin_inputs():
+    """the inputs every call below is made on (shared with the generator)"""
+    v = np.random.RandomState(0).randn(300)
+    v[10:14] = v[10]
+    rng = np.random.RandomState(2)
+    hashes = np.stack([np.sort(rng.randint(0, 900, 77)), rng.randint(0, 1 << 20, 77)], axis=1).astype(np.int32)
+    return dict(v=v, h=[(3, 0xABCDE), (9, 0x12345), (11, 0xFFFFF)], pk=[(5, 1.5), (200, 0.25), (255, 2.0)], hashes=hashes,
+                peaks=[(0, 3), (0, 250), (5, 77)])
+
+
 def test_surface_and_constants_equal_the_reference_module():
-    sys.path.insert(0, REF)
-    try:
-        import audfprint_analyze as R
-        for n in REF_NAMES:
-            assert hasattr(R, n), n
-            if isinstance(getattr(R, n), (int, float, str, bytes)):
-                assert getattr(R, n) == getattr(M, n), n
-        ra, ma = R.Analyzer(), M.Analyzer()
-        assert {k: v for k, v in vars(ra).items()} == {k: v for k, v in vars(ma).items()}
-        v = np.random.RandomState(0).randn(300)
-        v[10:14] = v[10]
-        assert np.array_equal(R.locmax(v), M.locmax(v))
-        assert np.array_equal(R.locmax(v, indices=True), M.locmax(v, indices=True))
-        h = [(3, 0xABCDE), (9, 0x12345), (11, 0xFFFFF)]
-        assert R.hashes2landmarks(h) == M.hashes2landmarks(h)
-        # the vector helpers (audfprint_analyze.py:153-197): same values, bit for bit
-        for width in (30.0, 4.0):
-            assert np.array_equal(ra.spreadpeaksinvector(v[:256], width), ma.spreadpeaksinvector(v[:256], width))
-        pk = [(5, 1.5), (200, 0.25), (255, 2.0)]
-        assert np.array_equal(ra.spreadpeaks(pk, npoints=256, width=30.0), ma.spreadpeaks(pk, npoints=256, width=30.0))
-        base = np.abs(v[:100])
-        assert np.array_equal(ra.spreadpeaks(pk[:1], width=7.0, base=base), ma.spreadpeaks(pk[:1], width=7.0, base=base))
-        assert {k: v_ for k, v_ in vars(ra).items() if not k.startswith('_Analyzer__')} == vars(ma)
-    finally:
-        sys.path.remove(REF)
-        for m in ('audfprint_analyze', 'stft', 'audio_read', 'hash_table'):
-            sys.modules.pop(m, None)
+    z, meta = _ref()
+    x = dropin_inputs()
+    assert sorted(meta['names']) == sorted(REF_NAMES)
+    for n in REF_NAMES:
+        assert hasattr(M, n), n
+        if n in meta['scalars']:
+            assert _scalar(meta['scalars'][n]) == getattr(M, n), n
+    ma = M.Analyzer()
+    assert {k: [type(v).__name__, v] for k, v in vars(ma).items()} == meta['analyzer_vars']
+    v = x['v']
+    assert np.array_equal(z['locmax'], M.locmax(v))
+    assert np.array_equal(z['locmax_indices'], M.locmax(v, indices=True))
+    assert [list(t) for t in M.hashes2landmarks(x['h'])] == meta['hashes2landmarks']
+    # the vector helpers (audfprint_analyze.py:153-197): same values, bit for bit
+    for width in (30.0, 4.0):
+        assert np.array_equal(z['spreadpeaksinvector_%g' % width], ma.spreadpeaksinvector(v[:256], width))
+    pk = x['pk']
+    assert np.array_equal(z['spreadpeaks'], ma.spreadpeaks(pk, npoints=256, width=30.0))
+    base = np.abs(v[:100])
+    assert np.array_equal(z['spreadpeaks_base'], ma.spreadpeaks(pk[:1], width=7.0, base=base))
+    assert {k: [type(v_).__name__, v_] for k, v_ in vars(ma).items()} == meta['analyzer_public_vars_after']
 
 
 def test_analyzer_pickles_and_holds_no_device_state():
@@ -94,26 +106,19 @@ def test_file_formats_roundtrip_and_bytes(tmp_path):
         M.peaks_load(fn)            # wrong magic
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not mounted')
 def test_file_bytes_equal_reference_writer(tmp_path):
-    sys.path.insert(0, REF)
-    try:
-        import audfprint_analyze as R
-        rng = np.random.RandomState(2)
-        hashes = np.stack([np.sort(rng.randint(0, 900, 77)), rng.randint(0, 1 << 20, 77)], axis=1).astype(np.int32)
-        a, b = str(tmp_path / 'a.afpt'), str(tmp_path / 'b.afpt')
-        R.hashes_save(a, hashes)
-        M.hashes_save(b, hashes)
-        assert open(a, 'rb').read() == open(b, 'rb').read()
-        assert R.hashes_load(b) == M.hashes_load(a)
-        pk = [(0, 3), (0, 250), (5, 77)]
-        R.peaks_save(a, pk)
-        M.peaks_save(b, pk)
-        assert open(a, 'rb').read() == open(b, 'rb').read() and R.peaks_load(b) == M.peaks_load(a)
-    finally:
-        sys.path.remove(REF)
-        for m in ('audfprint_analyze', 'stft', 'audio_read', 'hash_table'):
-            sys.modules.pop(m, None)
+    z, meta = _ref()
+    x = dropin_inputs()
+    a, b = str(tmp_path / 'a.afpt'), str(tmp_path / 'b.afpt')
+    with open(a, 'wb') as f:
+        f.write(z['afpt_bytes'].tobytes())                 # what the reference's hashes_save wrote
+    M.hashes_save(b, x['hashes'])
+    assert open(a, 'rb').read() == open(b, 'rb').read()
+    assert [list(t) for t in M.hashes_load(a)] == meta['hashes_load']        # (the reference's hashes_load of the same bytes)
+    with open(a, 'wb') as f:
+        f.write(z['afpk_bytes'].tobytes())
+    M.peaks_save(b, x['peaks'])
+    assert open(a, 'rb').read() == open(b, 'rb').read() and [list(t) for t in M.peaks_load(a)] == meta['peaks_load']
 
 
 def test_empty_input_shortcuts_need_no_gpu():

@@ -16,7 +16,7 @@ def test_two_ranks_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', AFP_BENCH_ONE_GPU='1', AFP_BENCH_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
            '--master-port', '29641', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2',
-           '--nclips', '96', '--secs', '10', '--pool', '96', '--c4-clips', '600', '--c4-batch', '200']
+           '--nclips', '96', '--secs', '10', '--pool', '96', '--c4-clips', '600', '--c4-batch', '200', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -61,7 +61,7 @@ def test_plain_gpus_2_launches_its_own_ranks():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
-           '--nclips', '64', '--secs', '5', '--pool', '64', '--no-table']
+           '--nclips', '64', '--secs', '5', '--pool', '64', '--no-table', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -93,7 +93,7 @@ def test_the_line_survives_a_crash_in_the_multi_rank_extras():
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', AFP_BENCH_ONE_GPU='1', AFP_BENCH_BACKEND='gloo', AFP_BENCH_CRASH_IN_EXTRAS='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
            '--master-port', '29643', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
-           '--nclips', '64', '--secs', '5', '--pool', '64', '--c4-clips', '200', '--c4-batch', '100']
+           '--nclips', '64', '--secs', '5', '--pool', '64', '--c4-clips', '200', '--c4-batch', '100', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode != 0                                   # rank 0 did die
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith('{')]

@@ -1,7 +1,7 @@
 """Vote counting of the matcher (second half): Matcher._best_count_ids /
 _approx_match_counts / match_hashes (audfprint_match.py:124-147, 241-352).
 CPU: the oracle restatement against the golden fixture made from the live reference
-(tests/golden/make_golden_match.py) and against the live reference on random hit lists; the host half of
+(tests/golden/make_golden_match.py) and against the reference's answers on random hit lists; the host half of
 audfprint_amd.match on a stand-in for the device.  GPU: audfprint_amd.match through the C ABI."""
 import os
 import random
@@ -54,14 +54,8 @@ def test_oracle_vote_counting_equals_reference_golden():
                 assert np.array_equal(got, z['s%d_q%d_res_e%d_t%d' % (si, qi, ec, tr)]), (si, qi, ec, tr)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not mounted')
-@pytest.mark.parametrize('seed', range(8))
-def test_oracle_vote_counting_equals_live_reference_on_random_hits(seed):
-    sys.path.insert(0, REF)
-    try:
-        import audfprint_match as RM
-    finally:
-        sys.path.remove(REF)
+def random_hits_case(seed):
+    """(hits, hashesperid, matcher switches) of random case `seed` (shared with tests/golden/make_golden_refcases.py)"""
     rng = np.random.RandomState(300 + seed)
     nids = int(rng.randint(1, 40))
     n = int(rng.randint(1, 4000))
@@ -69,24 +63,37 @@ def test_oracle_vote_counting_equals_live_reference_on_random_hits(seed):
     # a few ids get a concentrated skew (a "match"), the rest are spread out
     skew = np.where(rng.rand(n) < 0.4, (ids * 37) % 200 - 100 + rng.randint(-1, 2, n), rng.randint(-3000, 3000, n))
     hits = np.stack([ids, skew, rng.randint(0, 1 << 20, n), rng.randint(0, 500, n)], axis=1).astype(np.int32)
+    hashesperid = rng.randint(1, 3000, nids).astype(np.uint32)
+    sw = dict(window=int(rng.randint(0, 4)), threshcount=int(rng.randint(0, 8)), search_depth=int(rng.randint(1, 50)),
+              max_alignments_per_id=int(rng.randint(0, 5)))
+    return hits, hashesperid, sw
 
-    class HT(object):
-        hashesperid = rng.randint(1, 3000, nids).astype(np.uint32)
 
-    m = RM.Matcher()
-    m.window = int(rng.randint(0, 4)); m.threshcount = int(rng.randint(0, 8))
-    m.search_depth = int(rng.randint(1, 50)); m.max_alignments_per_id = int(rng.randint(0, 5))
-    rid, rraw = m._best_count_ids(hits, HT)
-    oid, oraw = O.match_best_count_ids(hits, HT.hashesperid, m.threshcount, m.search_depth)
-    assert np.array_equal(rid, oid) and np.array_equal(rraw, oraw)
-    assert np.array_equal(m._approx_match_counts(hits, rid, rraw),
-                          O.match_approx_counts(hits, oid, oraw, m.window, m.threshcount, m.max_alignments_per_id))
-    if m.threshcount >= 1:
+def hits_sha(hits, hashesperid):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(hits, '<i4').tobytes() + np.ascontiguousarray(hashesperid, '<u4').tobytes()).hexdigest()[:16]
+
+
+@pytest.mark.parametrize('seed', range(8))
+def test_oracle_vote_counting_equals_live_reference_on_random_hits(seed):
+    """the oracle against what the reference's own Matcher (_best_count_ids, _approx_match_counts, _exact_match_counts with
+    and without find_time_range) returned on the same random hit lists (tests/golden/reference_votes.npz)"""
+    import json
+    z = np.load(os.path.join(HERE, 'golden', 'reference_votes.npz'))
+    hits, hpi, sw = random_hits_case(seed)
+    assert json.loads(str(z['meta']))['hits_sha']['%d' % seed] == hits_sha(hits, hpi), 'input differs from the one the reference saw'
+    k = 'r%d_' % seed
+    oid, oraw = O.match_best_count_ids(hits, hpi, sw['threshcount'], sw['search_depth'])
+    assert np.array_equal(z[k + 'ids'], oid) and np.array_equal(z[k + 'raw'], oraw)
+    assert np.array_equal(z[k + 'approx'],
+                          O.match_approx_counts(hits, oid, oraw, sw['window'], sw['threshcount'], sw['max_alignments_per_id']))
+    if sw['threshcount'] >= 1:
         # the remaining modes on the same hit list (a threshold of 0 lets the reference index an empty time list: it raises)
         for tr in (False, True):
-            m.find_time_range = tr
-            assert np.array_equal(m._exact_match_counts(hits, rid, rraw),
-                                  O.match_exact_counts(hits, oid, oraw, m.window, m.threshcount, tr, m.time_quantile)), tr
+            assert np.array_equal(z[k + 'exact_t%d' % tr],
+                                  O.match_exact_counts(hits, oid, oraw, sw['window'], sw['threshcount'], tr, 0.02)), tr
+    else:
+        assert k + 'exact_t0' not in z.files
 
 
 class _FakeDevice(object):

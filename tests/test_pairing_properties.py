@@ -1,15 +1,12 @@
 """Integer stages (peaks2landmarks, landmarks2hashes, unique/sort) on random peak lists:
-CPU: oracle vs the live reference (hypothesis); GPU: afp_pairs_from_peaks vs the oracle."""
+CPU: oracle vs the reference's answers on seeded random peak lists; GPU: afp_pairs_from_peaks vs the oracle."""
+import hashlib
 import os
-import sys
 
 import numpy as np
 import pytest
-from hypothesis import given, settings, strategies as st
 
 from oracle import afp_oracle as O
-
-REF = '/root/reference'
 
 
 def _random_peaks(rng, nframes, density, maxk):
@@ -21,25 +18,43 @@ def _random_peaks(rng, nframes, density, maxk):
     return np.array(rows, dtype=np.int32).reshape(-1, 2)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not mounted')
-@settings(max_examples=40, deadline=None)
-@given(seed=st.integers(0, 10 ** 6), nframes=st.integers(1, 160), density=st.floats(0.05, 3.0),
-       fanout=st.integers(1, 12), targetdf=st.integers(1, 40), mindt=st.integers(0, 4), targetdt=st.integers(1, 70))
-def test_oracle_pairing_equals_reference(seed, nframes, density, fanout, targetdf, mindt, targetdt):
-    sys.path.insert(0, REF)
-    try:
-        import audfprint_analyze as R
-    finally:
-        sys.path.remove(REF)
+def pairing_case(kind, i):
+    """(peak list, peaks2landmarks switches) of case i: `plain` = sorted distinct bins per column, `list_order` = list-order
+    peaks with repeats and moved rows (shared with tests/golden/make_golden_refcases.py, which stores the reference's answers)"""
+    g = np.random.RandomState((7100 if kind == 'plain' else 7200) + i)
+    seed, nframes = int(g.randint(0, 10 ** 6 + 1)), int(g.randint(1, (160 if kind == 'plain' else 120) + 1))
+    density = float(g.uniform(0.05, 3.0))
+    kw = dict(maxpairsperpeak=int(g.randint(1, 13)), targetdf=int(g.randint(1, 41)), mindt=int(g.randint(0, 5)),
+              targetdt=int(g.randint(1, 71)))
     rng = np.random.RandomState(seed)
-    pk = _random_peaks(rng, nframes, density, 5)
-    an = R.Analyzer()
-    an.maxpairsperpeak, an.targetdf, an.mindt, an.targetdt = fanout, targetdf, mindt, targetdt
-    prm = O.Params(maxpairsperpeak=fanout, targetdf=targetdf, mindt=mindt, targetdt=targetdt)
-    ref_lm = an.peaks2landmarks([(int(c), int(b)) for c, b in pk])
-    got_lm = O.peaks2landmarks(pk, prm)
-    assert np.array_equal(np.array(ref_lm, dtype=np.int64).reshape(-1, 4), got_lm)
-    assert np.array_equal(R.landmarks2hashes(ref_lm), O.landmarks2hashes(got_lm))
+    pk = _random_peaks(rng, nframes, density, 5) if kind == 'plain' else _list_order_peaks(rng, nframes, density, 6, 0.2)
+    return pk, kw
+
+
+PAIRING_CASES = dict(plain=40, list_order=25)
+
+
+def peaks_sha(pk):
+    return hashlib.sha256(np.ascontiguousarray(pk, '<i4').tobytes()).hexdigest()[:16]
+
+
+def _pairing_equals_reference(kind):
+    """the oracle's landmarks and hashes against the reference's peaks2landmarks / landmarks2hashes on the same peak lists
+    (tests/golden/reference_pairing.npz)"""
+    import json
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_pairing.npz'))
+    sha = json.loads(str(z['meta']))['peaks_sha']
+    for i in range(PAIRING_CASES[kind]):
+        pk, kw = pairing_case(kind, i)
+        k = '%s%d_' % (kind, i)
+        assert sha[k] == peaks_sha(pk), 'input differs from the one the reference saw'
+        got_lm = O.peaks2landmarks(pk, O.Params(**kw))
+        assert np.array_equal(z[k + 'landmarks'], got_lm), k
+        assert np.array_equal(z[k + 'hashes'], O.landmarks2hashes(got_lm)), k
+
+
+def test_oracle_pairing_equals_reference():
+    _pairing_equals_reference('plain')
 
 
 @pytest.fixture(scope='module', params=['fused', 'generic'])
@@ -211,25 +226,8 @@ def _list_order_peaks(rng, nframes, density, maxk, dup_p):
     return rows
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not mounted')
-@settings(max_examples=25, deadline=None)
-@given(seed=st.integers(0, 10 ** 6), nframes=st.integers(1, 120), density=st.floats(0.05, 3.0),
-       fanout=st.integers(1, 12), targetdf=st.integers(1, 40), mindt=st.integers(0, 4), targetdt=st.integers(1, 70))
-def test_oracle_pairing_equals_reference_on_list_order_peaks(seed, nframes, density, fanout, targetdf, mindt, targetdt):
-    sys.path.insert(0, REF)
-    try:
-        import audfprint_analyze as R
-    finally:
-        sys.path.remove(REF)
-    rng = np.random.RandomState(seed)
-    pk = _list_order_peaks(rng, nframes, density, 6, 0.2)
-    an = R.Analyzer()
-    an.maxpairsperpeak, an.targetdf, an.mindt, an.targetdt = fanout, targetdf, mindt, targetdt
-    prm = O.Params(maxpairsperpeak=fanout, targetdf=targetdf, mindt=mindt, targetdt=targetdt)
-    ref_lm = an.peaks2landmarks([(int(c), int(b)) for c, b in pk])
-    got_lm = O.peaks2landmarks(pk, prm)
-    assert np.array_equal(np.array(ref_lm, dtype=np.int64).reshape(-1, 4), got_lm)
-    assert np.array_equal(R.landmarks2hashes(ref_lm), O.landmarks2hashes(got_lm))
+def test_oracle_pairing_equals_reference_on_list_order_peaks():
+    _pairing_equals_reference('list_order')
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 # A stale library (built from other sources than the tree's) is admitted for the comparison only (AFP_ALLOW_STALE_LIB).
 TAG=$1; A=$2; B=$3; N=${4:-2}; shift 4 2>/dev/null; [ "$1" = "--" ] && shift
 cd ${GRAFT_REPO_ROOT:-$PWD}; mkdir -p gpurun_out
-Q="--steps 300 --warmup 20 --no-cpu --no-c2 --no-extras --no-host --no-table $*"
+Q="--full --steps 300 --warmup 20 --no-cpu --no-c2 --no-extras --no-host --no-table $*"
 one() { AFP_LIB_PATH=$PWD/$1 AFP_ALLOW_STALE_LIB=1 python bench.py $Q 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = b['roofline']['kernels_ms']

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for mode in after before; do
   OUT=$PWD/gpurun_out/c4trace_$mode; rm -rf $OUT; mkdir -p $OUT
   if [ $mode = before ]; then export AFP_UPLOAD_STREAM=0 GPU_MAX_HW_QUEUES=4 AFP_DL_THREADS=1; else unset AFP_UPLOAD_STREAM GPU_MAX_HW_QUEUES AFP_DL_THREADS; fi
-  AFP_C4_TRACE=1 timeout 400 rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o t -- python bench.py --steps 3 --warmup 2 --no-cpu-all --cpu-sample 4 --no-host --no-c2 --extras c4_job > $OUT/log.txt 2> $OUT/err.txt
+  AFP_C4_TRACE=1 timeout 400 rocprofv3 --output-format csv --kernel-trace --memory-copy-trace -d $OUT -o t -- python bench.py --full --steps 3 --warmup 2 --no-cpu-all --cpu-sample 4 --no-host --no-c2 --extras c4_job > $OUT/log.txt 2> $OUT/err.txt
   { echo "# $mode: AFP_UPLOAD_STREAM=${AFP_UPLOAD_STREAM:-1} GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-12 (set by the package)} AFP_DL_THREADS=${AFP_DL_THREADS:-8}; build $(python -c 'from audfprint_amd import build; print(build.source_id())' 2>/dev/null)";
     python - $OUT/log.txt <<'PY'
 import json, sys

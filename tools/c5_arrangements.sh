@@ -3,7 +3,7 @@
 # kernels, 7.7-7.9 ms pipelined) share the chip: the scan + pairing stages on a CU range of their own (--cu-split N: the
 # spectral stage gets the other 256 - N compute units), against the default (all stages on all CUs), 200 steps x 2, alternating.
 cd ${GRAFT_REPO_ROOT:-$PWD}; mkdir -p gpurun_out
-Q="--workload c5 --steps 200 --warmup 12 --no-cpu --no-c2 --no-extras --no-host --no-table"
+Q="--full --workload c5 --steps 200 --warmup 12 --no-cpu --no-c2 --no-extras --no-host --no-table"
 one() { python bench.py $Q "$@" 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = b['roofline']['kernels_ms']

@@ -3,7 +3,7 @@
 #     gpurun --timeout 1500 -- 'bash tools/gpu_call.sh r06a tests bench prof'
 # usage: tools/gpu_call.sh <tag> <step> [<step> ...]      everything lands in gpurun_out/<tag>_*
 #   tests        python -m pytest tests -m gpu                      -> <tag>_gpu_tests.log
-#   bench        python bench.py (the default, extras included)     -> <tag>_bench.json + a one-screen summary
+#   bench        python bench.py --full (extras included)           -> results/<tag>_bench.json + a one-screen summary
 #   driver       python bench.py --gpus 1 --steps 20 --warmup 5     -> <tag>_bench_driver_style.json (what the driver runs)
 #   prof         tools/prof_all.sh <tag> (kernel trace + PMC passes of c3 / c5 / c4 / c2, one-file traces)
 #   soak[:N]     tools/soak.py, N iterations (default 700) of the shipped configuration
@@ -18,7 +18,7 @@ summary() {
 python - "$1" <<'PY'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
-r = b['roofline']
+r = b.get('roofline', {})
 print('c3', b['ms_per_step'], 'ms', b['value'], 'hashes/s | roofline', {k: r.get(k) for k in ('bound', 'achieved', 'frac', 'traffic', 'kernel_ms', 'whole_step_frac', 'traffic_over_algorithmic', 'profile_build_id')}, b['build_id'])
 p = b.get('parity', {})
 print('parity', {k: p.get(k) for k in ('clips_checked', 'bit_exact', 'timed_variant_checked', 'guarded_pass_identical', 'near_tie_units', 'tie_prone_units')})
@@ -42,7 +42,7 @@ PY
 for step in "$@"; do
   case $step in
     tests)  timeout 900 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}_gpu_tests.log 2>&1; echo "tests rc $?"; tail -4 gpurun_out/${TAG}_gpu_tests.log ;;
-    bench)  timeout 300 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "bench rc $?"; tail -3 gpurun_out/${TAG}_bench.err; summary gpurun_out/${TAG}_bench.json ;;
+    bench)  R=results/${TAG}_bench; mkdir -p results; timeout 600 python bench.py --full > $R.json 2> $R.err; echo "bench rc $?"; tail -3 $R.err; summary $R.json ;;
     driver) T0=$SECONDS; timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver_style.json 2> gpurun_out/${TAG}_bench_driver_style.err; echo "driver rc $? (whole command $((SECONDS - T0)) s)"; tail -2 gpurun_out/${TAG}_bench_driver_style.err; summary gpurun_out/${TAG}_bench_driver_style.json ;;
     prof)   timeout 400 bash tools/prof_all.sh ${TAG} > gpurun_out/prof_all_${TAG}.log 2>&1; echo "prof rc $?"; head -3 gpurun_out/prof_all_${TAG}.log ;;
     soak*)  N=${step#soak:}; [ "$N" = "soak" ] && N=700
